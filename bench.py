@@ -31,6 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "speech-emotion-privacy-trust_amd"))
 
 SR, CLIP_L, HOP, WIN, SHIFT = 16000, 80000, 160, 200, 50
 MFMA_PEAK, HBM_PEAK = 2.5e15, 8.0e12
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: everything written, at most
 
 
 def build(F, device, seed=8):
@@ -131,6 +132,21 @@ def cpu_baseline(F, seconds_budget=30.0):
             "one_thread": {"value": v1, "unit": "utterances/s", "cores": 1,
                            "sample": f"same work on 1 thread: median of {n1} steps; mel {t_mel1*1e3:.2f} ms/clip, "
                                      f"step {t_step1:.3f} s"}}
+
+
+def dump_outputs(path, trainer, loss, p1, p2):
+    """What the timed step hands its caller -- the loss and the two networks' logits -- plus the trainable parameters
+    it updated, copied to the host right after the timed region (later sections of the run replay the step again)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rows = p1.shape[0]
+    room = (DUMP_MAX_BYTES - 4096 - 4 * (1 + trainer.flat.flat.numel())) // (4 * (p1[0].numel() + p2[0].numel()))  # 4096: .npy headers
+    if room < rows:   # a larger batch than fits: the same fixed, seeded sample of windows from both networks
+        keep = torch.randperm(rows, generator=torch.Generator().manual_seed(8))[:room].sort().values.to(p1.device)
+        p1, p2 = p1[keep], p2[keep]
+    out = {"loss": loss.reshape(1), "emotion_logits": p1, "gender_logits": p2, "trainable_params": trainer.flat.flat}
+    for name, t in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.detach().float().cpu().numpy())
 
 
 def secondary(a, dev):
@@ -250,7 +266,13 @@ def main():
                     help="profiling aid: warm-up, capture, then ONLY graph replays (no probe / eager timing / serialised "
                          "steps / mel-256 / cpu baseline), so a rocprofv3 kernel trace of the run is the replayed step; "
                          "tools/replay_stats.py cuts the replay window out of it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the LAST timed step computed (loss, both networks' logits, the updated trainable "
+                         "parameters) as DIR/<name>.npy in float32, rank 0; the inputs are seeded, so two builds can be "
+                         "compared output for output (fused workload only)")
     a = ap.parse_args()
+    if a.dump_outputs and a.workload != "fused":
+        ap.error("--dump-outputs covers the fused workload")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # launched bare (`python bench.py --gpus N`): start the N ranks ourselves -- BEFORE anything touches the
@@ -341,9 +363,11 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            step_fn()
+            loss, p1, p2 = step_fn()
         barrier()
         dt = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, trainer, loss, p1, p2)
         if rank == 0:
             emit(({"mode": "replay-only", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                               "ms_per_step": round(dt / a.steps * 1e3, 3), "value": round(clips * world * a.steps / dt, 2),
@@ -394,14 +418,14 @@ def main():
     for _ in range(a.steps):
         th = time.perf_counter()
         if step_fn is not None:
-            loss, _, _ = step_fn()
+            loss, p1, p2 = step_fn()
         else:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             x = pipe.features(wav)
             e1.record()
             mel_ev.append((e0, e1))
-            loss, _, _ = trainer.train_step(x.view(Bw, 1, WIN, F), le, lg, weights)
+            loss, p1, p2 = trainer.train_step(x.view(Bw, 1, WIN, F), le, lg, weights)
         host_s += time.perf_counter() - th   # enqueue time only (no sync inside the step)
     barrier()
     dt = time.perf_counter() - t0
@@ -410,6 +434,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     loss_val = float(loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer, loss, p1, p2)
 
     # ---- the same K steps fed from PINNED HOST batches (the reference moves every batch host -> device inside its loop,
     # training_cloak_with_grl.py:125-132): two distinct host batches alternate; the next one crosses PCIe on a copy stream

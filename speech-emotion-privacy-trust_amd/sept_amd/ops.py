@@ -8,6 +8,10 @@ from ._lib import SeptError, lib, check, current_stream_ptr, require_cuda
 
 
 def _s(t):
+    # every launch asks for its stream here: a host tensor is refused with SeptError, on a machine with a GPU too
+    # (where torch's current_stream(cpu) would raise a ValueError instead)
+    if not t.is_cuda:
+        require_cuda(t)
     return current_stream_ptr(t.device)
 
 

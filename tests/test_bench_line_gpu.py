@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +26,8 @@ def _run(*flags):
 
 
 @pytest.mark.parametrize("rehearse", [False, True])
-def test_one_json_line_with_the_contract_fields(rehearse):
-    d, err = _run(*(["--dp-rehearse"] if rehearse else []))
+def test_one_json_line_with_the_contract_fields(rehearse, tmp_path):
+    d, err = _run(*(["--dp-rehearse"] if rehearse else ["--dump-outputs", str(tmp_path)]))
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
@@ -43,3 +44,11 @@ def test_one_json_line_with_the_contract_fields(rehearse):
         assert "rehearse" in d["config"]["parallelism"]
     else:
         assert d["dp"] is None and d["config"]["parallelism"] == "dp1"
+        # --dump-outputs: the last timed step's results, float32, within the size cap
+        got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+        assert sorted(got) == ["emotion_logits", "gender_logits", "loss", "trainable_params"]
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+        assert sum(f.stat().st_size for f in tmp_path.glob("*.npy")) <= 64 << 20
+        Bw = d["config"]["windows_per_gpu"]
+        assert got["emotion_logits"].shape == (Bw, 4) and got["gender_logits"].shape == (Bw, 2)
+        assert abs(float(got["loss"][0]) - d["config"]["loss"]) < 1e-5      # the loss the line reports: the same step

@@ -114,7 +114,9 @@ def test_dp_shard_average_equals_global_batch_gloo():
     """world_size 2 on CPU (gloo): averaging the flat gradient buffers of equal shards equals the
     global-batch gradient (the loss is a mean over the local batch and the scale term is batch
     independent -- training_cloak_with_grl.py:150-160)."""
-    mgr = mp.Manager()
+    # spawn, not fork: on a GPU machine this process may already hold an initialised HIP runtime (GPU tests run
+    # in the same session), and a forked child of such a process is unsafe
+    mgr = mp.get_context("spawn").Manager()
     ret = mgr.dict()
     port = 29500 + os.getpid() % 2000
     mp.spawn(_dp_worker, args=(2, port, 16, ret), nprocs=2, join=True)
@@ -133,3 +135,15 @@ def test_pool_first_gate_knows_the_backward_kernels_limits():
         assert ops.conv1_pool_supported(H, Wd) and not ops.conv1_pool_supported(H, Wd, backward=True), (H, Wd)
     assert not ops.conv1_pool_supported(201, 80) and not ops.conv1_pool_supported(200, 72, backward=True)
     assert sept_amd.lib.sept_conv1_coef_floats() == 2800     # SEPT_CONV1_COEF_FLOATS; ops sizes the scratch from the query
+
+
+def test_capture_forks_follow_the_runtime_queue_limit(monkeypatch):
+    """A process limited to fewer than the runtime's default four hardware queues captures the step on one stream
+    (functional.CAPTURE_FORKS); with the default, or more, the capture forks.  Host-side only."""
+    from sept_amd import functional as SF
+    for value, want in ((None, True), ("4", True), ("8", True), ("2", False), ("1", False), ("x", False)):
+        if value is None:
+            monkeypatch.delenv("GPU_MAX_HW_QUEUES", raising=False)
+        else:
+            monkeypatch.setenv("GPU_MAX_HW_QUEUES", value)
+        assert SF._capture_forks() is want, value
