@@ -68,6 +68,10 @@ int sept_mel_forward(const sept_mel_plan* plan, const float* wav, int B, int L, 
                      int layout, void* stream);
 /* name of the device kernel sept_mel_forward launches for this plan (for rocprof filters) */
 const char* sept_mel_kernel_name(const sept_mel_plan* plan);
+/* read-only: the kernel (and its tile depth in frames, tile_out nullable) that sept_mel_forward
+ * would launch for B clips of L samples.  The transpose form picks a deep or a shallow tile per
+ * launch from B and T; the shuffle form always launches sept_mel_kernel_name(plan). */
+const char* sept_mel_launch_kernel_name(const sept_mel_plan* plan, int B, int L, int* tile_out);
 
 /* ------------------------------------------------------------------------------------
  * Conv stack of two_d_cnn_lstm (model/baseline_models.py:171-189): Conv2d(k=5, pad=2) on

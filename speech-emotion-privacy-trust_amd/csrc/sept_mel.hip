@@ -1152,6 +1152,38 @@ extern "C" const char* sept_mel_kernel_name(const sept_mel_plan* plan) {
   return plan ? plan->kernel_name : "";
 }
 
+namespace {
+struct MelLaunch {
+  const void* kernel;
+  const char* name;
+  size_t smem;
+  int tile;
+};
+// tile depth: workgroups are persistent, so a launch costs rounds = ceil(tiles / resident workgroups) tile times; a
+// small batch (the 32-clip training step: 672 deep tiles on 512 workgroups = 2 rounds) is shorter with the half-size
+// tile (1344 tiles = 3 rounds of half the length, plus its larger staging share)
+MelLaunch mel_launch_of(const sept_mel_plan* plan, int B, int T) {
+  MelLaunch l{plan->kernel, plan->kernel_name, plan->smem, plan->tile};
+  if (plan->kernel_s) {
+    auto rounds = [&](int t, size_t sm) {
+      const long n = long(B) * ((T + t - 1) / t);
+      const long res = 256L * (sm <= 80 * 1024 ? 2 : 1);
+      return double((n + res - 1) / res);
+    };
+    if (1.12 * rounds(plan->tile_s, plan->smem_s) * plan->tile_s < rounds(plan->tile, plan->smem) * plan->tile)
+      l = MelLaunch{plan->kernel_s, plan->kernel_name_s, plan->smem_s, plan->tile_s};
+  }
+  return l;
+}
+}  // namespace
+
+extern "C" const char* sept_mel_launch_kernel_name(const sept_mel_plan* plan, int B, int L, int* tile_out) {
+  if (!plan || B < 0 || L < 0) return "";
+  const MelLaunch l = mel_launch_of(plan, B, 1 + L / plan->hop);
+  if (tile_out) *tile_out = l.tile;
+  return l.name;
+}
+
 extern "C" int sept_mel_forward(const sept_mel_plan* plan, const float* wav, int B, int L, float* out,
                                 int layout, void* stream) {
   SEPT_REQUIRE(plan, SEPT_ERR_INVALID, "sept_mel_forward: null plan");
@@ -1178,24 +1210,10 @@ extern "C" int sept_mel_forward(const sept_mel_plan* plan, const float* wav, int
   a.T = 1 + L / plan->hop;
   a.F = plan->n_mels;
   a.layout = layout;
-  // tile depth: workgroups are persistent, so a launch costs rounds = ceil(tiles / resident workgroups) tile times; a
-  // small batch (the 32-clip training step: 672 deep tiles on 512 workgroups = 2 rounds) is shorter with the half-size
-  // tile (1344 tiles = 3 rounds of half the length, plus its larger staging share)
-  const void* kernel = plan->kernel;
-  size_t smem = plan->smem;
-  int tile = plan->tile;
-  if (plan->kernel_s) {
-    auto rounds = [&](int t, size_t sm) {
-      const long n = long(B) * ((a.T + t - 1) / t);
-      const long res = 256L * (sm <= 80 * 1024 ? 2 : 1);
-      return double((n + res - 1) / res);
-    };
-    if (1.12 * rounds(plan->tile_s, plan->smem_s) * plan->tile_s < rounds(plan->tile, plan->smem) * plan->tile) {
-      kernel = plan->kernel_s;
-      smem = plan->smem_s;
-      tile = plan->tile_s;
-    }
-  }
+  const MelLaunch launch = mel_launch_of(plan, B, a.T);
+  const void* kernel = launch.kernel;
+  const size_t smem = launch.smem;
+  const int tile = launch.tile;
   a.tiles_per_clip = (a.T + tile - 1) / tile;
   // persistent workgroups (per-lane window / twiddle tables are loaded once, then many tiles)
   const long n_tiles = long(B) * a.tiles_per_clip;

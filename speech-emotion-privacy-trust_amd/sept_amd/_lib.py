@@ -43,6 +43,7 @@ SIGNATURES = {
     "sept_mel_num_frames": (c_int, [c_void_p, c_int]),
     "sept_mel_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "sept_mel_kernel_name": (c_char_p, [c_void_p]),
+    "sept_mel_launch_kernel_name": (c_char_p, [c_void_p, c_int, c_int, POINTER(c_int)]),
     "sept_conv5x5_prep_weights": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sept_prepare_operands": (c_int, [POINTER(PrepItem), c_int, c_void_p]),
     "sept_conv5x5_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

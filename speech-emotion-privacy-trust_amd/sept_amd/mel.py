@@ -32,6 +32,12 @@ class MelPlan:
     def kernel_name(self) -> str:
         return lib.sept_mel_kernel_name(self._h).decode()
 
+    def launch_kernel(self, batch: int, length: int):
+        """(kernel name, tile depth in frames) that forward() launches for `batch` clips of `length` samples."""
+        tile = ctypes.c_int(0)
+        name = lib.sept_mel_launch_kernel_name(self._h, int(batch), int(length), ctypes.byref(tile)).decode()
+        return name, tile.value
+
     def num_frames(self, length: int) -> int:
         return check(lib.sept_mel_num_frames(self._h, int(length)), "sept_mel_num_frames")
 
