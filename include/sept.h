@@ -323,6 +323,16 @@ int sept_conv5x5_forward_act(const void* ext, const float* mean, const float* in
  * pixels, waves over output channels, taps per barrier (0 / negative: double-buffered), input-channel slices, LDS bytes.
  * Returns 0, or SEPT_ERR_UNSUPPORTED when the channel pair (or its statistics form, want_stats != 0) has no kernel. */
 int sept_conv5x5_variant(int W, int cin, int cout, int want_stats, int* out);
+/* Which kernel a LAUNCH runs (host-only): the index of its entry in the tile table, from the same choice the launch makes
+ * (including the half-size tiles of launches under 192 workgroups).  form: 0 plain, 1 epilogue (statistics for forward
+ * shapes, BatchNorm backward sums for data-gradient shapes), 2 BatchNorm-apply loader (sept_conv5x5_dgrad_bnapply),
+ * 3 the same with the sums epilogue, 4 activation loader (sept_conv5x5_forward_act), 5 the same with statistics.
+ * out[7] = pb, wp, wn, taps per barrier, slices, LDS bytes, pixels per tile.  Returns the index, or SEPT_ERR_UNSUPPORTED
+ * ("no kernel") when that launch would be refused, SEPT_ERR_INVALID for bad arguments. */
+int sept_conv5x5_launch_variant(int B, int H, int W, int cin, int cout, int form, int* out);
+/* Entry i of the tile table: out[8] = cin, cout, pb, wp, wn, taps per barrier, slices, bitmask of the instantiated forms
+ * (bit f = form f above).  Returns 0, or SEPT_ERR_UNSUPPORTED past the last entry. */
+int sept_conv5x5_variant_table(int i, int* out);
 int sept_conv5x5_dgrad_bnsums(const void* dy_out, const void* wt, void* dx_out, const void* ypool, const float* bn_gamma,
                               const float* bn_beta, const float* dropscale, float* partials, int B, int H, int W, int cin,
                               int cout, void* stream);

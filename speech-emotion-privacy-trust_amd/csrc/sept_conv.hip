@@ -686,6 +686,12 @@ const ConvVariant* conv_pick_launch(int B, int H, int W, int cin, int cout, bool
   return v;
 }
 
+// The kernel function of a table entry for a launch form (null: the entry has no such form).  want_lbn as conv_pick.
+const void* conv_form_fn(const ConvVariant* v, bool stats, int want_lbn) {
+  return want_lbn == 2 ? (stats ? v->fn_act_stats : v->fn_act)
+                       : want_lbn == 1 ? (stats ? v->fn_lbn_stats : v->fn_lbn) : (stats ? v->fn_stats : v->fn);
+}
+
 struct ConvLbn {   // the BatchNorm block whose backward apply pass (LBN; g, sums set) or forward activation (LACT; g, sums
   const void* g;   // null) runs in the tile loader
   const float *sums, *mean, *invstd, *gamma, *beta, *drop;
@@ -708,8 +714,7 @@ int conv_launch(const char* who, const void* x, const void* wt, const float* bia
                "%s: no kernel for cin=%d cout=%d W=%d (supported channel pairs: 32->64, "
                "64->128, 64->32, 128->64, 128->128; statistics form: see sept_conv5x5_stats_parts)", who, cin, cout, W);
   const bool act = lbn && !lbn->g;
-  const void* fn = act ? (stats ? best->fn_act_stats : best->fn_act)
-                       : lbn ? (stats ? best->fn_lbn_stats : best->fn_lbn) : (stats ? best->fn_stats : best->fn);
+  const void* fn = conv_form_fn(best, stats != nullptr, lbn ? (lbn->g ? 1 : 2) : 0);
   SEPT_REQUIRE(fn, SEPT_ERR_UNSUPPORTED, "%s: no kernel form for cin=%d cout=%d", who, cin, cout);
   ConvArgs a;
   a.lg = nullptr;
@@ -787,6 +792,38 @@ extern "C" int sept_conv5x5_variant(int W, int cin, int cout, int want_stats, in
   const ConvVariant* v = conv_pick(W, cin, cout, want_stats != 0, &smem);
   SEPT_REQUIRE(v, SEPT_ERR_UNSUPPORTED, "sept_conv5x5_variant: no kernel for cin=%d cout=%d W=%d stats=%d", cin, cout, W, want_stats);
   out[0] = v->pb; out[1] = v->wp; out[2] = v->wn; out[3] = v->tg; out[4] = v->cs; out[5] = int(smem);
+  return SEPT_OK;
+}
+
+// The table entry a LAUNCH of this shape and form runs: the same conv_pick_launch / conv_form_fn that conv_launch calls.
+extern "C" int sept_conv5x5_launch_variant(int B, int H, int W, int cin, int cout, int form, int* out) {
+  SEPT_REQUIRE(out && B > 0 && H > 0 && W > 0 && form >= 0 && form <= 5, SEPT_ERR_INVALID,
+               "sept_conv5x5_launch_variant: null argument / B=%d H=%d W=%d form=%d", B, H, W, form);
+  SEPT_REQUIRE(B <= 65528, SEPT_ERR_UNSUPPORTED, "sept_conv5x5_launch_variant: B=%d exceeds grid.y", B);
+  const bool stats = form & 1;
+  const int want_lbn = form >> 1;   // 0 plain loader, 1 BatchNorm apply (LBN), 2 activation (LACT)
+  SEPT_REQUIRE(want_lbn != 1 || (H % 2 == 0 && W % 2 == 0), SEPT_ERR_UNSUPPORTED,
+               "sept_conv5x5_launch_variant: no kernel: H=%d W=%d (the loader form needs whole 2x2 windows)", H, W);
+  size_t smem = 0;
+  const ConvVariant* v = conv_pick_launch(B, H, W, cin, cout, stats, &smem, want_lbn);
+  SEPT_REQUIRE(v && conv_form_fn(v, stats, want_lbn), SEPT_ERR_UNSUPPORTED,
+               "sept_conv5x5_launch_variant: no kernel for cin=%d cout=%d W=%d form=%d", cin, cout, W, form);
+  out[0] = v->pb; out[1] = v->wp; out[2] = v->wn; out[3] = v->tg; out[4] = v->cs; out[5] = int(smem);
+  out[6] = 32 * v->pb * v->wp;
+  return int(v - kConvVariants);
+}
+
+// Entry i of the tile table: cin, cout, pb, wp, wn, tg, cs and a bitmask of its instantiated forms (bit f = form f of
+// sept_conv5x5_launch_variant).
+extern "C" int sept_conv5x5_variant_table(int i, int* out) {
+  constexpr int n = int(sizeof(kConvVariants) / sizeof(kConvVariants[0]));
+  SEPT_REQUIRE(out && i >= 0, SEPT_ERR_INVALID, "sept_conv5x5_variant_table: null argument / i=%d", i);
+  SEPT_REQUIRE(i < n, SEPT_ERR_UNSUPPORTED, "sept_conv5x5_variant_table: i=%d past the %d entries", i, n);
+  const ConvVariant& v = kConvVariants[i];
+  out[0] = v.cin; out[1] = v.cout; out[2] = v.pb; out[3] = v.wp; out[4] = v.wn; out[5] = v.tg; out[6] = v.cs;
+  const void* fns[6] = {v.fn, v.fn_stats, v.fn_lbn, v.fn_lbn_stats, v.fn_act, v.fn_act_stats};
+  out[7] = 0;
+  for (int f = 0; f < 6; ++f) out[7] |= fns[f] ? 1 << f : 0;
   return SEPT_OK;
 }
 

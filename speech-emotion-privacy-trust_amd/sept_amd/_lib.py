@@ -147,6 +147,8 @@ SIGNATURES = {
                                c_float, c_int, c_float, c_void_p]),
     "sept_conv5x5_bwsums_parts": (c_int, [c_int] * 5),
     "sept_conv5x5_variant": (c_int, [c_int] * 4 + [POINTER(c_int)]),
+    "sept_conv5x5_launch_variant": (c_int, [c_int] * 6 + [POINTER(c_int)]),
+    "sept_conv5x5_variant_table": (c_int, [c_int, POINTER(c_int)]),
     "sept_conv5x5_bnapply_parts": (c_int, [c_int] * 6),
     "sept_conv5x5_act_parts": (c_int, [c_int] * 6),
     "sept_conv5x5_forward_act": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p]),
